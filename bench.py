@@ -518,6 +518,43 @@ def self_spawn(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _dump_sample(a, n):
+    """`a` whole when it has at most n elements, else n of them at fixed, seeded, sorted positions (the same positions in
+    every run with the same sizes)."""
+    a = a.reshape(-1)
+    if a.numel() <= n:
+        return a
+    idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(a.numel(), n, replace=False))
+    return a[torch.from_numpy(idx).to(a.device)]
+
+
+def dump_outputs(trainer, directory):
+    """What the timed step computed in its last step, as DIR/<name>.npy (float32 / float64): the loss it returned and its
+    three terms, the model's decoder logits, the parameters it updated, the gradient and Adam moments it left behind and
+    the batch-norm moving statistics.  The gradient and moments are a seeded sample of 2^20 values each, so that the
+    files stay under DUMP_BUDGET_BYTES together."""
+    m = trainer.model
+    P = m.params
+    arrays = [('loss', m.loss.double()), ('loss_terms', m._terms.double()), ('pred_program', m.pred_program)]
+    if m.multitask:
+        arrays += [('pred_action', m.pred_action), ('pred_per', m.pred_per)]
+    arrays += [('params', _dump_sample(P.flat, 12500000)), ('grad', _dump_sample(P.grad, 1 << 20)),
+               ('adam_m', _dump_sample(P.m, 1 << 20)), ('adam_v', _dump_sample(P.v, 1 << 20)),
+               ('bn_moving', m.moving_flat)]
+    host = [(n, np.ascontiguousarray(t.detach().cpu().numpy())) for n, t in arrays]
+    total = sum(a.nbytes for _, a in host)
+    assert total <= DUMP_BUDGET_BYTES, 'dump of %d bytes exceeds the %d byte budget' % (total, DUMP_BUDGET_BYTES)
+    os.makedirs(directory, exist_ok=True)
+    for n, a in host:
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        np.save(os.path.join(directory, n + '.npy'), a)
+    return [n for n, _ in host]
+
+
 def log(msg):
     if os.environ.get('RANK', '0') == '0':
         sys.stderr.write('[bench %.1fs] %s\n' % (time.time() - _T0, msg))
@@ -550,7 +587,12 @@ def main():
     ap.add_argument('--frames', default='uint8', choices=['uint8', 'float32'],
                     help='precision the demonstration frames are staged in: uint8 = the dataset\'s own (Karel states are '
                          'booleans, ViZDoom frames bytes), widened on load inside conv1; float32 = the reference\'s feed dtype')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (loss, logits, parameters, a seeded '
+                         'sample of the gradient and Adam moments, batch-norm moving statistics) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if 'WORLD_SIZE' not in os.environ and (args.gpus > 1 or args.self_spawn):
         self_spawn(args)
 
@@ -615,6 +657,9 @@ def main():
     # a persistent LSTM launch that gave up a hand-off: the guarded step skipped it on the device and the trainer
     # re-ran it on the per-step kernels INSIDE the timed region (count reported; 0 on a dedicated GPU)
     persist_fallbacks = trainer.settle()
+    if args.dump_outputs and dp.rank == 0:
+        names = dump_outputs(trainer, args.dump_outputs)
+        log('wrote %s to %s' % (', '.join(names), args.dump_outputs))
 
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     step_stats = {'median': round(per_step[len(per_step) // 2], 4), 'p10': round(per_step[len(per_step) // 10], 4),

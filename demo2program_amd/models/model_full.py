@@ -796,7 +796,9 @@ class Model(object):
         return loss
 
     def _side_stream(self):
-        if not self.use_side_stream:
+        # (a captured step runs on the capturing stream alone: replaying a graph whose capture forked work onto a second
+        #  stream crashed the HIP runtime)
+        if not self.use_side_stream or torch.cuda.is_current_stream_capturing():
             return torch.cuda.current_stream()
         if getattr(self, '_side', None) is None:
             self._side = pick_concurrent_stream()
