@@ -851,9 +851,15 @@ static int launch_wgrad(const ConvGeom& g, const T* x, const float* dy, float* d
     return 1;
 }
 
+bool d2p_conv_direct_wgrad_bn_ok(const ConvGeom& g, int G, int seq) {
+    if (G < 1 || seq < 1 || g.N < 1 || g.N % (G * seq) != 0) return false;
+    return d2p_conv_rows_wgrad_affine_ok(g) || d2p_conv_wide_wgrad_affine_ok(g, G, seq);
+}
+
 int d2p_conv_direct_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw, void* ws,
                           size_t ws_bytes, hipStream_t st, const ConvBnFold* bn) {
     if (bn) {       // (input affine: the row-strip kernel of the 16 -> 32 layer, the wide kernel of the 48-channel layers)
+        if (!d2p_conv_direct_wgrad_bn_ok(g, bn->G, bn->seq)) return 0;
         const int rc = d2p_conv_rows_wgrad(g, x, x_is_u8, dy, dw, ws, ws_bytes, st, bn);
         return rc != 0 ? rc : d2p_conv_wide_wgrad(g, x, x_is_u8, dy, dw, ws, ws_bytes, st, bn);
     }

@@ -56,6 +56,9 @@ int d2p_conv_direct_dgrad(const ConvGeom& g, const float* dy, const float* w, fl
 int d2p_conv_direct_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw,
                           void* ws, size_t ws_bytes, hipStream_t st, const ConvBnFold* bn = nullptr);
 size_t d2p_conv_direct_wgrad_ws(const ConvGeom& g);
+// a weight-gradient launch with the input affine (ConvBnFold::in_scale) has a kernel at this geometry and (G, seq); the
+// folding branch of d2p_conv_direct_wgrad answers from it, and so does d2p_conv_bn_affine_ok
+bool d2p_conv_direct_wgrad_bn_ok(const ConvGeom& g, int G, int seq);
 void d2p_conv_direct_enable(int fwd, int dgrad, int wgrad);
 
 // Whole-frame back end (conv_frames.hip): same return convention; tried first when the
@@ -71,6 +74,7 @@ void d2p_conv_frames_tune(int tiles_per_wave);
 int d2p_conv_rows_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw, void* ws,
                         size_t ws_bytes, hipStream_t st, const ConvBnFold* bn = nullptr);
 size_t d2p_conv_rows_wgrad_ws(const ConvGeom& g);
+bool d2p_conv_rows_wgrad_affine_ok(const ConvGeom& g);
 int d2p_conv_rows_wgrad_bnbwd(const ConvGeom& g, const void* x, int x_is_u8, const float* act, const float* dy,
                               const float* coef, int G, int seq, float* dw, float* dbias, void* ws, size_t ws_bytes,
                               hipStream_t st);
@@ -100,6 +104,7 @@ void d2p_conv_wide_set_fwd2(int on);
 int d2p_conv_wide_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw, void* ws, size_t ws_bytes,
                         hipStream_t st, const ConvBnFold* bn = nullptr);
 size_t d2p_conv_wide_wgrad_ws(const ConvGeom& g);
+bool d2p_conv_wide_wgrad_affine_ok(const ConvGeom& g, int G, int seq);
 
 // floor(n / d) for 0 <= n < 2^31 and d >= 1 by multiply-high + shift (exact: m = ceil(2^(31+s) / d),
 // s = ceil(log2 d)).  An integer division costs ~25 VALU instructions on gfx950; the implicit-GEMM

@@ -918,13 +918,16 @@ int d2p_conv_rows_wgrad_bnbwd(const ConvGeom& g, const void* x, int x_is_u8, con
     return RowsWgrad<4, 16, 80, float, 1024>::run_bnbwd(g, (const float*)x, act, dy, coef, G, seq, dw, dbias, ws, ws_bytes, st);
 }
 
+// the weight gradient through the previous layer's batch-norm apply: RowsWgrad<16, 32, 40> only
+bool d2p_conv_rows_wgrad_affine_ok(const ConvGeom& g) { return rows_key(g) == 2 && g.N >= 1; }
+
 int d2p_conv_rows_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw, void* ws,
                         size_t ws_bytes, hipStream_t st, const ConvBnFold* bn) {
     const int key = rows_key(g);
     if (!key || g.N < 1) return 0;
     if (((uintptr_t)x & 15) || ((uintptr_t)dy & 3)) return 0;
     if (bn && bn->in_scale) {
-        if (key != 2 || x_is_u8 || (((uintptr_t)bn->in_scale | (uintptr_t)bn->in_shift) & 15)) return 0;
+        if (!d2p_conv_rows_wgrad_affine_ok(g) || x_is_u8 || (((uintptr_t)bn->in_scale | (uintptr_t)bn->in_shift) & 15)) return 0;
         return RowsWgrad<16, 32, 40, float, 512>::run(g, (const float*)x, dy, dw, ws, ws_bytes, st, bn);
     }
     if (key == 1) {

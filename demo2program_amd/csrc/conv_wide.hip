@@ -1010,13 +1010,20 @@ size_t d2p_conv_wide_wgrad_ws(const ConvGeom& g) {
     return (size_t)wide_cus() * 9 * g.Cin * WCO * sizeof(float);
 }
 
+// the weight gradient through the previous layer's batch-norm apply: G * S workgroups (S >= 1) with the workspace of
+// d2p_conv_wide_wgrad_ws, sized for one per CU -- so at most one index per CU (more would need a workspace per G)
+bool d2p_conv_wide_wgrad_affine_ok(const ConvGeom& g, int G, int seq) {
+    return wide_wgrad_ok(g) && g.N >= 1 && G >= 1 && seq >= 1 && g.N % (G * seq) == 0 && G <= wide_cus() &&
+           wide_wg_fb(g, seq) >= 1;
+}
+
 // bn (optional): in_scale / in_shift = the input read through the previous layer's batch-norm apply (the pad pixels behind x)
 int d2p_conv_wide_wgrad(const ConvGeom& g, const void* x, int x_is_u8, const float* dy, float* dw, void* ws, size_t ws_bytes,
                         hipStream_t st, const ConvBnFold* bn) {
     if (x_is_u8 || !wide_wgrad_ok(g)) return 0;
     if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15)) return 0;
     if (bn) {
-        if (bn->G < 1 || bn->seq < 1 || g.N % (bn->G * bn->seq) != 0 || bn->G > 4096 || !bn->in_scale) return 0;
+        if (!bn->in_scale || !d2p_conv_wide_wgrad_affine_ok(g, bn->G, bn->seq)) return 0;
         if (((uintptr_t)bn->in_scale) & 15) return 0;
     }
     if (g.N == 0) return 0;

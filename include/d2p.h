@@ -303,7 +303,8 @@ int d2p_rn_fc1_bwd(int B, int k, int U, const float* y1a, const float* dy1, cons
  * Same values as the separate launches up to the order of the fp64 sums / one fp32 rounding of the affine. */
 int d2p_conv_bn_slices(int N, int H, int W, int Cin, int Cout, int G, int seq);
 /* 1 when this layer's folding forward and weight-gradient launches read their input through the previous layer's batch-norm
- * apply (in_scale / in_shift + the G pad pixels behind x): the caller then never writes the normalised tensor. */
+ * apply (in_scale / in_shift + the G pad pixels behind x): the caller then never writes the normalised tensor.  Answered from
+ * the weight-gradient launch's own conditions: the 16 -> 32 layer at W == 40, the 48-channel layers with G <= CUs. */
 int d2p_conv_bn_affine_ok(int N, int H, int W, int Cin, int Cout, int G, int seq);
 int d2p_conv2d_nhwc_s2_same_fwd_bn(int N, int H, int W, int Cin, int Cout, const void* x, int x_is_u8, const float* w,
                                    const float* bias, int act, float* y, int G, int seq, const float* in_scale,

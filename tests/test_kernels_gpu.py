@@ -516,6 +516,289 @@ def test_batch_norm_folded_into_the_conv_launches(K, B, G, T):
         K.conv_fwd_bn(dev(rnd(N, 8, 8, 16)), dev(rnd(3, 3, 16, 16)), dev(rnd(16)), G, T, 1, st1, act=1)
 
 
+# ------------------------------------------------------------------ the batch-norm-folded conv launches: fp64 reference
+def _bn_index(N, G, seq):
+    """demonstration index of every frame: frames are (batch, index, step) with step fastest"""
+    return (torch.arange(N) // seq) % G
+
+
+def _bn_fold_conv_ref(x, w, b, G, seq, sc=None, sh=None):
+    """lrelu(conv(x') + b) in fp64, x' = x * sc[g] + sh[g] when an input affine is given: the previous layer's batch-norm
+    apply, so the out-of-image taps see the NORMALISED tensor's zero padding (the pad pixel -sh / sc of the pre-norm one)"""
+    x = x.double()
+    if sc is not None:
+        grp = _bn_index(x.shape[0], G, seq)
+        C = x.shape[3]
+        x = x * sc.double()[grp].view(-1, 1, 1, C) + sh.double()[grp].view(-1, 1, 1, C)
+    return x, oracle.lrelu(_conv_ref(x, w.double(), b.double()))
+
+
+def _bn_fold_stats_ref(a, G, seq, eps=1e-3):
+    """per-index mean, biased variance and rstd [G, C] of the (post-lrelu, pre-norm) activation a"""
+    a = a.double().cpu()
+    grp = _bn_index(a.shape[0], G, seq)
+    C = a.shape[-1]
+    mean = torch.stack([a[grp == gi].reshape(-1, C).mean(0) for gi in range(G)])
+    var = torch.stack([a[grp == gi].reshape(-1, C).var(0, unbiased=False) for gi in range(G)])
+    return mean, var, 1.0 / torch.sqrt(var + eps)
+
+
+def _bn_fold_bwd_ref(a, dy, gamma, G, seq, eps=1e-3):
+    """the batch-norm backward of y = gamma * xhat + beta over a per index, then lrelu' (a has the sign of the
+    pre-activation): (da, dgamma, dbeta, dbias = sum da)"""
+    a, dy = a.double().cpu(), dy.double().cpu()
+    grp = _bn_index(a.shape[0], G, seq)
+    C = a.shape[-1]
+    mean, _, rstd = _bn_fold_stats_ref(a, G, seq, eps)
+    xh = (a - mean[grp].view(-1, 1, 1, C)) * rstd[grp].view(-1, 1, 1, C)
+    da = torch.zeros_like(a)
+    for gi in range(G):
+        sel = grp == gi
+        d, x_ = dy[sel].reshape(-1, C), xh[sel].reshape(-1, C)
+        dx = gamma.double() * rstd[gi] * (d - d.mean(0) - x_ * (d * x_).mean(0))
+        da[sel] = dx.reshape(da[sel].shape)
+    da = da * torch.where(a > 0, torch.ones_like(a), torch.full_like(a, 0.2))
+    return da, (dy * xh).reshape(-1, C).sum(0), dy.reshape(-1, C).sum(0), da.reshape(-1, C).sum(0)
+
+
+def _bn_fold_dgrad_sums_ref(dx, act, mean, rstd, G, seq):
+    """[G, C, 2]: (sum dX, sum dX * xhat) per (index, channel), xhat = (act - mean) * rstd of the layer beneath"""
+    dx, act = dx.double().cpu(), act.double().cpu()
+    grp = _bn_index(dx.shape[0], G, seq)
+    C = dx.shape[-1]
+    out = torch.zeros(G, C, 2, dtype=torch.float64)
+    for gi in range(G):
+        sel = grp == gi
+        xh = (act[sel] - mean[gi].double().cpu()) * rstd[gi].double().cpu()
+        out[gi, :, 0] = dx[sel].reshape(-1, C).sum(0)
+        out[gi, :, 1] = (dx[sel] * xh).reshape(-1, C).sum(0)
+    return out
+
+
+def _guarded(*shape, dtype=torch.float32):
+    """a NaN-filled buffer with 1024 guard elements behind the view the launch may write"""
+    n = int(np.prod(shape))
+    full = torch.full((n + 1024,), float('nan'), dtype=dtype, device='cuda')
+    return full[:n].view(*shape), full
+
+
+def _untouched_behind(full, n):
+    assert torch.isnan(full[n:]).all(), 'a launch wrote behind its output'
+
+
+def _refused(fn, full):
+    """the launch raises D2P_EINVAL and writes nothing"""
+    from demo2program_amd.lib import D2PError
+    with pytest.raises(D2PError, match=r'\(code -1\)'):
+        fn()
+    torch.cuda.synchronize()
+    assert torch.isnan(full).all(), 'a refused launch wrote its output'
+
+
+# (Cin, Cout, H, W, G, seq, sequences per index, extra frames); G = 'cus' / 'cus+44': the device's CU count (+ 44)
+_FOLD_CASES = [
+    # 4 -> 16 (conv1): row strips, odd and short H; seq * Ho odd leaves sequences of 40 * odd pixels, no whole 16-pixel
+    # tiles (refused).  (The "four tiles at least" edge of d2p_conv_bn_slices cannot be met: a whole-tile sequence of
+    # conv1 has 80 pixels at least, and the 16 -> 32 forward of H * W >= 400 is the block form's, without that rule.)
+    (4, 16, 80, 80, 1, 1, 2, 0), (4, 16, 80, 80, 2, 3, 1, 0), (4, 16, 80, 80, 5, 4, 1, 0),
+    (4, 16, 37, 80, 2, 3, 1, 0), (4, 16, 37, 80, 5, 4, 1, 0), (4, 16, 37, 80, 1, 1, 2, 0),
+    (4, 16, 61, 80, 28, 2, 1, 0), (4, 16, 61, 80, 1, 1, 1, 0),
+    (4, 16, 6, 80, 10, 20, 1, 0), (4, 16, 6, 80, 2, 3, 1, 0), (4, 16, 6, 80, 28, 2, 1, 0),
+    (4, 16, 80, 80, 2, 3, 1, 1),                                  # N not a multiple of G * seq
+    # 16 -> 32 at W = 40: block-form forward, RowsWgrad<16, 32, 40> with the affine, row-strip / block dgrad with sums
+    (16, 32, 40, 40, 2, 3, 1, 0), (16, 32, 40, 40, 5, 4, 1, 0), (16, 32, 21, 40, 5, 4, 1, 0), (16, 32, 21, 40, 28, 2, 1, 0),
+    (16, 32, 31, 40, 2, 3, 1, 0), (16, 32, 31, 40, 1, 1, 2, 0), (16, 32, 3, 40, 10, 20, 1, 0), (16, 32, 3, 40, 2, 3, 1, 0),
+    (16, 32, 40, 40, 2, 3, 1, 3),                                 # N not a multiple of G * seq
+    # 16 -> 32 block form at W != 40: statistics out, but no weight-gradient kernel takes the affine
+    (16, 32, 20, 20, 2, 3, 1, 0), (16, 32, 20, 20, 28, 2, 1, 0), (16, 32, 24, 24, 5, 4, 1, 0), (16, 32, 30, 30, 1, 1, 2, 0),
+    (16, 32, 21, 19, 2, 3, 1, 0),
+    # the 48-channel layers; masked last tile where seq * Ho * Wo % 16 != 0
+    (32, 48, 20, 20, 2, 3, 1, 0), (32, 48, 20, 20, 10, 20, 1, 0), (32, 48, 16, 20, 5, 4, 1, 0), (32, 48, 4, 5, 'cus+44', 2, 1, 0),
+    (48, 48, 10, 10, 28, 2, 1, 0), (48, 48, 8, 10, 10, 20, 1, 0), (48, 48, 5, 5, 5, 4, 1, 0), (48, 48, 4, 5, 2, 3, 1, 0),
+    (48, 48, 9, 6, 1, 1, 2, 0), (48, 48, 3, 3, 2, 3, 1, 0), (48, 48, 5, 5, 'cus', 1, 1, 0), (48, 48, 5, 5, 'cus+44', 1, 1, 0),
+    (48, 48, 10, 10, 'cus', 2, 1, 0),
+    (48, 48, 10, 10, 5, 4, 1, 7),                                 # N not a multiple of G * seq
+]
+
+
+@pytest.mark.parametrize('Cin,Cout,H,W,G,seq,B,extra', _FOLD_CASES)
+def test_batch_norm_folded_conv_launches_keep_their_predicates(K, Cin, Cout, H, W, G, seq, B, extra):
+    """The contract of the four predicates in conv.hip over the geometries the folded launches take: a predicate's yes means
+    its launch runs and matches the fp64 reference (d2p_conv_bn_slices: d2p_conv2d_nhwc_s2_same_fwd_bn with and without an
+    input affine, and the statistics; d2p_conv_bn_affine_ok: the weight gradient through that affine;
+    d2p_conv_dgrad_bn_slices: the input gradient and the batch-norm-backward sums of the layer beneath;
+    d2p_conv_bnbwd_ok: the first layer's batch-norm backward inside its weight gradient), its no that the launch refuses
+    with D2P_EINVAL and writes nothing."""
+    if isinstance(G, str):
+        G = torch.cuda.get_device_properties(0).multi_processor_count + (44 if G.endswith('+44') else 0)
+    N = B * G * seq + extra
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    whole = extra == 0
+    grp = _bn_index(N, G, seq)
+    S = K.conv_bn_slices((N, H, W, Cin), Cout, G, seq)
+    aff_ok = K.conv_bn_affine_ok((N, H, W, Cin), Cout, G, seq)
+    Sd = K.conv_dgrad_bn_slices((N, H, W, Cin), Cout, G, seq)
+    bb_ok = K.conv_bnbwd_ok((N, H, W, Cin), Cout)
+    assert S >= 0 and Sd >= 0
+    assert not aff_ok or S > 0, 'the affine is promised for a forward that is not taken'
+    if not whole:
+        assert S == 0 and not aff_ok and Sd == 0
+    w = rnd(3, 3, Cin, Cout, seed=31, scale=0.02 if Cin == 4 else 0.1)
+    b = rnd(Cout, seed=32)
+    gam, bet = rnd(Cout, seed=33) + 1.0, rnd(Cout, seed=34)
+    dy = rnd(N, Ho, Wo, Cout, seed=35)
+    frames = [('f32', rnd(N, H, W, Cin, seed=30))]
+    if Cin == 4:
+        g = torch.Generator().manual_seed(36)
+        xu = torch.randint(0, 256, (N, H, W, Cin), generator=g, dtype=torch.uint8)
+        xu[..., 3] = 0
+        frames.append(('u8', xu))
+    n_out = N * Ho * Wo * Cout
+
+    # ---- forward with statistics, without an input affine
+    a_kern = None
+    for kind, x in frames:
+        xd = x.cuda() if kind == 'u8' else dev(x)
+        a, a_full = _guarded(N, Ho, Wo, Cout)
+        if S == 0:
+            st = torch.zeros(G * Cout * 2, dtype=torch.float64, device='cuda')
+            _refused(lambda: K.conv_fwd_bn(xd, dev(w), dev(b), G, seq, 1, st, act=1, out=a), a_full)
+            continue
+        st = torch.zeros(G * S * Cout * 2, dtype=torch.float64, device='cuda')
+        K.conv_fwd_bn(xd, dev(w), dev(b), G, seq, S, st, act=1, out=a)
+        torch.cuda.synchronize()
+        _untouched_behind(a_full, n_out)
+        _, ref = _bn_fold_conv_ref(x, w, b, G, seq)
+        close(a, ref, atol=1e-4 * max(1.0, float(ref.abs().max()) / 100))
+        assert torch.equal(a, K.conv_fwd(xd, dev(w), dev(b), act=1))          # the same products in the same order
+        mean, rstd, var, sc, sh, pad = (torch.empty(G, Cout, device='cuda') for _ in range(6))
+        K.bn_stats_from_partials(st, N // G * Ho * Wo, Cout, G, S, dev(gam), dev(bet), mean, rstd, var, affine=(sc, sh, pad))
+        mu, vv, rs = _bn_fold_stats_ref(a, G, seq)
+        if kind == 'f32':
+            a_kern, mean_k, rstd_k = a, mean.clone(), rstd.clone()
+        mean, rstd, var, sc, sh, pad = (t.double().cpu() for t in (mean, rstd, var, sc, sh, pad))
+        for gi in range(G):
+            close(mean[gi], mu[gi], atol=1e-6 * float(mu[gi].abs().max()) + 1e-7)
+            close(var[gi], vv[gi], rtol=1e-5, atol=1e-7)
+            close(rstd[gi], rs[gi], rtol=1e-5)
+            close(sc[gi], gam.double() * rs[gi], rtol=1e-5)
+            close(sh[gi], bet.double() - mu[gi] * gam.double() * rs[gi], rtol=1e-4, atol=1e-5)
+            close(pad[gi], -sh[gi] / sc[gi], rtol=1e-6, atol=1e-7)
+
+    # ---- the input read through the previous layer's batch-norm apply: forward and weight gradient
+    x = frames[0][1]
+    sc = rnd(G, Cin, seed=37).abs() + 0.5
+    sh = rnd(G, Cin, seed=38)
+    x_ext = torch.empty(N * H * W * Cin + G * Cin, device='cuda')
+    xd, xpad = x_ext[:N * H * W * Cin].view(N, H, W, Cin), x_ext[N * H * W * Cin:].view(G, Cin)
+    xd.copy_(dev(x))
+    xpad.copy_(dev(-sh / sc))
+    dw, dw_full = _guarded(3, 3, Cin, Cout)
+    if aff_ok:
+        xn, ref = _bn_fold_conv_ref(x, w, b, G, seq, sc, sh)
+        a2, a2_full = _guarded(N, Ho, Wo, Cout)
+        st2 = torch.zeros(G * S * Cout * 2, dtype=torch.float64, device='cuda')
+        K.conv_fwd_bn(xd, dev(w), dev(b), G, seq, S, st2, act=1, out=a2, in_affine=(dev(sc), dev(sh), xpad))
+        torch.cuda.synchronize()
+        _untouched_behind(a2_full, n_out)
+        close(a2, ref, atol=2e-5 * float(ref.abs().max()) + 1e-4)
+        mean2, rstd2 = torch.empty(G, Cout, device='cuda'), torch.empty(G, Cout, device='cuda')
+        K.bn_stats_from_partials(st2, N // G * Ho * Wo, Cout, G, S, None, None, mean2, rstd2)
+        mu, _, rs = _bn_fold_stats_ref(a2, G, seq)
+        mean2, rstd2 = mean2.double().cpu(), rstd2.double().cpu()
+        for gi in range(G):
+            close(mean2[gi], mu[gi], atol=1e-6 * float(mu[gi].abs().max()) + 1e-7)
+            close(rstd2[gi], rs[gi], rtol=1e-5)
+        xr, wr = xn.clone().requires_grad_(True), w.double().requires_grad_(True)
+        _conv_ref(xr, wr, b.double()).backward(dy)
+        K.conv_wgrad_bn(xd, dev(dy), dw, G, seq, (dev(sc), dev(sh)))
+        torch.cuda.synchronize()
+        _untouched_behind(dw_full, dw.numel())
+        close(dw, wr.grad, atol=2e-5 * float(wr.grad.abs().max()) + 1e-4, rtol=1e-5)
+    elif S > 0:         # (the forward is taken: the no is the weight gradient's)
+        _refused(lambda: K.conv_wgrad_bn(xd, dev(dy), dw, G, seq, (dev(sc), dev(sh))), dw_full)
+    else:               # (no folded forward: the weight gradient through an affine either refuses or is right)
+        from demo2program_amd.lib import D2PError
+        try:
+            K.conv_wgrad_bn(xd, dev(dy), dw, G, seq, (dev(sc), dev(sh)))
+        except D2PError as e:
+            assert '(code -1)' in str(e), e
+            torch.cuda.synchronize()
+            assert torch.isnan(dw_full).all(), 'a refused launch wrote its output'
+        else:
+            torch.cuda.synchronize()
+            _untouched_behind(dw_full, dw.numel())
+            xn, _ = _bn_fold_conv_ref(x, w, b, G, seq, sc, sh)
+            wr = w.double().requires_grad_(True)
+            _conv_ref(xn, wr, b.double()).backward(dy)
+            close(dw, wr.grad, atol=2e-5 * float(wr.grad.abs().max()) + 1e-4, rtol=1e-5)
+
+    # ---- the input gradient with the batch-norm-backward sums of the layer beneath
+    act = rnd(N, H, W, Cin, seed=39)
+    mu_b, rs_b = rnd(G, Cin, seed=40), rnd(G, Cin, seed=41).abs() + 0.5
+    dx, dx_full = _guarded(N, H, W, Cin)
+    if Sd > 0:
+        std = torch.zeros(G * Sd * Cin * 2, dtype=torch.float64, device='cuda')
+        K.conv_dgrad_bn(dev(dy), dev(w), (N, H, W, Cin), dev(act), dev(mu_b), dev(rs_b), G, seq, std, Sd, dx=dx)
+        torch.cuda.synchronize()
+        _untouched_behind(dx_full, dx.numel())
+        assert torch.equal(dx, K.conv_dgrad(dev(dy), dev(w), (N, H, W, Cin)))
+        xr = x.double().requires_grad_(True)
+        _conv_ref(xr, w.double(), b.double()).backward(dy)
+        close(dx, xr.grad, atol=1e-4)
+        got = std.view(G, Sd, Cin, 2).sum(1).cpu()
+        want = _bn_fold_dgrad_sums_ref(xr.grad, act, mu_b, rs_b, G, seq)
+        for gi in range(G):
+            scale = float(xr.grad[grp == gi].abs().sum(dim=(0, 1, 2)).max())
+            close(got[gi, :, 0], want[gi, :, 0], atol=2e-6 * scale + 1e-5, rtol=1e-5)
+            close(got[gi, :, 1], want[gi, :, 1], atol=1e-5 * scale + 1e-5, rtol=1e-5)
+    else:
+        std = torch.zeros(G * Cin * 2, dtype=torch.float64, device='cuda')
+        _refused(lambda: K.conv_dgrad_bn(dev(dy), dev(w), (N, H, W, Cin), dev(act), dev(mu_b), dev(rs_b), G, seq, std, 1,
+                                         dx=dx), dx_full)
+
+    # ---- the first layer's batch-norm backward inside its weight gradient (dy: the gradient w.r.t. its batch-norm output)
+    dwb, dwb_full = _guarded(3, 3, Cin, Cout)
+    if bb_ok and whole:
+        R, inner = N * Ho * Wo, seq * Ho * Wo
+        if a_kern is None:          # (no folded forward at this (G, seq): the plain one, statistics in fp64)
+            a_kern = K.conv_fwd(dev(x), dev(w), dev(b), act=1)
+            mu, _, rs = _bn_fold_stats_ref(a_kern, G, seq)
+            mean_k, rstd_k = dev(mu), dev(rs)
+        da64, dg64, db64, dbias64 = _bn_fold_bwd_ref(a_kern, dy, gam, G, seq)
+        dyd = dev(dy)
+        sums = [None]
+        # the same sums left by the input gradient of the layer above (16 -> 32 at Ho x Wo), where that launch exists
+        Sd2 = K.conv_dgrad_bn_slices((N, Ho, Wo, Cout), 32, G, seq)
+        if Sd2 > 0:
+            dy2 = rnd(N, (Ho + 1) // 2, (Wo + 1) // 2, 32, seed=42)
+            w2 = rnd(3, 3, Cout, 32, seed=43, scale=0.1)
+            st_ = torch.zeros(G * Sd2 * Cout * 2, dtype=torch.float64, device='cuda')
+            dyd = K.conv_dgrad_bn(dev(dy2), dev(w2), (N, Ho, Wo, Cout), a_kern, mean_k, rstd_k, G, seq, st_, Sd2)
+            da64, dg64, db64, dbias64 = _bn_fold_bwd_ref(a_kern, dyd, gam, G, seq)
+            sums.append((st_, Sd2))
+        wr = torch.zeros(3, 3, Cin, Cout, dtype=torch.float64, requires_grad=True)
+        _conv_ref(x.double(), wr, torch.zeros(Cout, dtype=torch.float64)).backward(da64)
+        xh_abs = ((a_kern.double().cpu() - mean_k.double().cpu()[grp].view(-1, 1, 1, Cout)).abs() *
+                  rstd_k.double().cpu()[grp].view(-1, 1, 1, Cout))
+        dy_abs = dyd.double().cpu().abs()
+        for sm in sums:
+            coef = torch.empty(G, Cout, 4, device='cuda')
+            dg, db, dbias = (torch.empty(Cout, device='cuda') for _ in range(3))
+            K.bn_bwd_coef(a_kern.view(R, Cout), dyd.reshape(R, Cout), dev(gam), mean_k, rstd_k, G, inner, coef, dg, db, sums=sm)
+            K.conv_wgrad_bnbwd(dev(x), a_kern, dyd.reshape(N, Ho, Wo, Cout), coef, G, seq, dwb, dbias)
+            torch.cuda.synchronize()
+            _untouched_behind(dwb_full, dwb.numel())
+            close(dg, dg64, atol=1e-5 * float((dy_abs * xh_abs).reshape(-1, Cout).sum(0).max()) + 1e-6)
+            close(db, db64, atol=1e-5 * float(dy_abs.reshape(-1, Cout).sum(0).max()) + 1e-6)
+            close(dwb, wr.grad, atol=1e-4 * float(wr.grad.abs().max()))
+            close(dbias, dbias64, atol=1e-4 * float(da64.abs().max()) * 40)
+    else:
+        coef = torch.zeros(G, Cout, 4, device='cuda')
+        a_any = dev(rnd(N, Ho, Wo, Cout, seed=44))
+        _refused(lambda: K.conv_wgrad_bnbwd(dev(x), a_any, dev(dy), coef, G, seq, dwb, None), dwb_full)
+
+
 # ------------------------------------------------------------------ scheduled sampling
 def test_sched_sample_statistics(K):
     """d2p_sched_sample: p = 0 keeps the ground truth, p = 1 always draws, the draw frequencies

@@ -30,9 +30,11 @@ def _maxerr(a, b):
     return (a.detach().double().cpu() - b.detach().double().cpu()).abs().max().item()
 
 
-def _check_against_oracle(cfg, params, batch, out, grads, logit_tol=1e-4):
+def _check_against_oracle(cfg, params, batch, out, grads, logit_tol=1e-4, fold_bn=None):
     from demo2program_amd.models.model_full import Model
     model = Model(cfg, params=params)
+    if fold_bn is not None:
+        model.fold_bn = fold_bn
     feed = model.get_feed_dict(batch)
     loss = model.forward(feed)
     model.backward()
@@ -950,6 +952,30 @@ def test_batch_norm_folded_into_the_conv_launches_equals_the_separate_launches()
         scale = float(res[0][1][n].abs().max()) + 1e-12
         assert float((res[0][1][n] - res[1][1][n]).abs().max()) <= 5e-5 * scale, n
     torch.testing.assert_close(res[0][2], res[1][2], rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize('h,w,folded,affine', [
+    (61, 80, ('conv1', 'conv2', 'conv3', 'conv4', 'conv5'), ('conv1', 'conv2', 'conv3', 'conv4')),
+    (40, 40, ('conv2', 'conv3', 'conv4', 'conv5'), ('conv2', 'conv3', 'conv4'))])
+def test_batch_norm_folded_at_untried_vizdoom_geometries_matches_oracle(h, w, folded, affine):
+    """Model.fold_bn at frame sizes the other model tests never run.  61x80: conv1 / conv2 fold through the row-strip
+    kernels with odd H (31x40), conv3-5 read 16x20, 8x10 and 4x5 through the affine.  40x40: conv1 is not folded, conv2
+    runs the block-form forward at 20x20 and conv3 reads its output through the affine.  Against the fp64 oracle, and the
+    step with the separate launches gives the same loss and gradients."""
+    cfg, params, batch = small_case('vizdoom', seed=67, h=h, w=w, batch_size=2, k=3, max_demo_len=4, max_program_len=6)
+    out, grads = run_oracle(cfg, params, batch)
+    m, _ = _check_against_oracle(cfg, params, batch, out, grads, fold_bn=True)
+    for l in range(1, 6):
+        name = 'conv%d' % l
+        assert (name + '/bn_partial' in m._bufs) == (name in folded), name
+        assert (name + '/bn_scale' in m._bufs) == (name in affine), name
+    # (the separate launches: the same oracle checks, loss included, and the gradients against the folded step's)
+    g_fold = {n: t.clone() for n, t in m.params.g.items()}
+    m2, _ = _check_against_oracle(cfg, params, batch, out, grads, fold_bn=False)
+    assert not any(k.endswith('/bn_partial') for k in m2._bufs)
+    for n, t in g_fold.items():
+        scale = float(t.abs().max()) + 1e-12
+        assert float((m2.params.g[n] - t).abs().max()) <= 2e-4 * scale + 1e-6, n
 
 
 def test_k25_demonstrations_match_oracle():
