@@ -757,6 +757,62 @@ def argmax_rows(x2d, out=None):
     return out
 
 
+def karel_exec_supported(B, L, h, w, depth):
+    """The device program metrics take this geometry (d2p_karel_exec_ws_bytes != 0; no GPU needed)."""
+    return call.d2p_karel_exec_ws_bytes(B, L, h, w, depth) != 0
+
+
+def karel_exec(tokens, p_len, is_same, demos, demo_len, demos2=None, demo2_len=None, make_error=True, T_out=0,
+               calls=False, frames=False, keep_failed=False, depth=16):
+    """Karel syntax / execution / demo comparison of a program set in one launch (d2p.h d2p_karel_exec).
+
+    tokens [B, L] int32, p_len [B], is_same [B] int32; demos [B, k, T, h, w, cs] uint8 or float32 (the first depth
+    channels; the launch takes depth 16 only) with demo_len [B, k]; demos2 / demo2_len the same for a second demo set (or None).  Returns a dict
+    of device tensors: syntax [B], exec_len / is_correct [B, k + k2], num_correct [B, 2] (int32), and when asked for
+    calls / frames [B, k + k2] int32 and execution [B, k + k2, T_out, h, w, 16] float32.  Reads the row status words
+    back (one synchronisation): a row without Karel raises IndexError as the host world does, a row that hit a step
+    bound raises RuntimeError."""
+    _require_gpu(tokens, p_len, is_same, demos, demo_len, demos2, demo2_len)
+    B, L = tokens.shape
+    _, k, T, h, w, cs = demos.shape
+    dev = tokens.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    for t in (tokens, p_len, is_same, demo_len, demo2_len):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError('karel_exec: index tensors must be contiguous int32')
+    for t in (demos, demos2):
+        if t is not None and (t.dtype not in (torch.uint8, torch.float32) or not t.is_contiguous()):
+            raise ValueError('karel_exec: demo frames must be contiguous uint8 or float32')
+    k2, T2, cs2 = (0, 0, 0) if demos2 is None else (demos2.shape[1], demos2.shape[2], demos2.shape[5])
+    if demos2 is not None and tuple(demos2.shape[3:5]) != (h, w):
+        raise ValueError('karel_exec: both demo sets need the same grid')
+    kk = k + k2
+    flags = ((1 if make_error else 0) | (2 if demos.dtype == torch.uint8 else 0) |
+             (4 if demos2 is not None and demos2.dtype == torch.uint8 else 0) | (8 if keep_failed else 0))
+    out = dict(syntax=torch.empty(B, **i32), exec_len=torch.empty(B, kk, **i32),
+               is_correct=torch.empty(B, kk, **i32), num_correct=torch.empty(B, 2, **i32))
+    if calls:
+        out['calls'] = torch.empty(B, kk, **i32)
+    if frames:
+        out['frames'] = torch.empty(B, kk, **i32)
+    if T_out:
+        out['execution'] = torch.empty(B, kk, T_out, h, w, 16, dtype=torch.float32, device=dev)
+    wsb = call.d2p_karel_exec_ws_bytes(B, L, h, w, depth)
+    status = torch.empty(max(wsb, 4) // 4, **i32)          # (the workspace is the row status words)
+    call.d2p_karel_exec(B, L, ptr(tokens), tokens.stride(0), ptr(p_len), ptr(is_same), h, w, depth,
+                        flags, k, T, ptr(demos), cs, ptr(demo_len), k2, T2, ptr(demos2), cs2, ptr(demo2_len),
+                        ptr(out['syntax']), ptr(out['exec_len']), ptr(out['is_correct']), ptr(out['num_correct']),
+                        ptr(out.get('calls')), ptr(out.get('frames')), ptr(out.get('execution')), int(T_out),
+                        ptr(status), status.numel() * 4, current_stream())
+    st = status[:B].cpu().numpy()
+    if (st & 3).any():
+        raise IndexError('no Karel in the world (program row %d)' % int(np.flatnonzero(st & 3)[0]))
+    if (st & 12).any():
+        raise RuntimeError('karel_exec: program row %d hit a parser / interpreter step bound'
+                           % int(np.flatnonzero(st & 12)[0]))
+    return out
+
+
 # ---------------------------------------------------------------- losses
 def _lab_strides(kind, V, T):
     # program labels [B,V,L]; action/per labels [B,k,T,V] flattened to rows r=(b,i)

@@ -1908,10 +1908,19 @@ class Model(object):
         if with_programs:
             vocab = self.vocab
             make_error = getattr(c, 'env_type', None) != 'no_error'
-            # the feed keeps depth%4 frames padded to NHWC4 (get_feed_dict); metrics see the real depth
-            s_h = f['s_h'].view(B, k, T, c.h, c.w, -1)[..., :c.depth].float().cpu().numpy()
+            # Karel: syntax and execution metrics in one launch per program set, on the frames where they live
+            # (program_metrics.karel_device_metrics); D2P_HOST_PROGRAM_METRICS=1 = the host functions
+            device_metrics = karel and not flag('D2P_HOST_PROGRAM_METRICS')
+            s_h_dev = f['s_h'].view(B, k, T, c.h, c.w, -1)
             host = f.get('host', {})
-            test = None
+            test = test_dev = None
+            cache = {}
+
+            def s_h_host():
+                # the feed keeps depth%4 frames padded to NHWC4 (get_feed_dict); metrics see the real depth
+                if 's_h' not in cache:
+                    cache['s_h'] = s_h_dev[..., :c.depth].float().cpu().numpy()
+                return cache['s_h']
 
             def host_np(name):
                 v = host[name]
@@ -1924,17 +1933,43 @@ class Model(object):
                 ts = ts.cpu().numpy() if torch.is_tensor(ts) else np.asarray(ts)
                 tl = host['test_demo_len']
                 tl = tl.cpu().numpy() if torch.is_tensor(tl) else np.asarray(tl)
-                test = (ts.astype(np.float32), tl.astype(np.int32).reshape(B, -1))
+                test = (ts, tl.astype(np.int32).reshape(B, -1))
+                if device_metrics:
+                    # uploaded once per report, shared by both program sets
+                    td = torch.from_numpy(np.ascontiguousarray(ts if ts.dtype in (np.uint8, np.float32)
+                                                               else ts.astype(np.float32)))
+                    test_dev = (td.to('cuda'), torch.from_numpy(test[1]).to('cuda'))
 
         def program_block(prefix, st, p_len):
             """syntax / exact / execution metrics of one decoded program set"""
-            syn = PM.check_correct_syntax(vocab, st['pred_tokens'], p_len, st['is_same_seq'], parse=parse)
+            dev = None
+            if device_metrics:
+                dev = PM.karel_device_metrics(st['pred_tokens'], p_len, st['is_same_seq'], s_h_dev, f['demo_len'],
+                                              *(test_dev or (None, None)), make_error=make_error)
+            if dev is not None:
+                syn = dev['syntax']
+            else:
+                syn = PM.check_correct_syntax(vocab, st['pred_tokens'], p_len, st['is_same_seq'], parse=parse)
+            # (exact-program comparison stays on the host: canonical forms unroll WHILE; it parses syntax-correct rows)
             exact = PM.exact_program_compare(vocab, st['pred_tokens'], p_len, syn, gt_tokens, plen, parse=parse)
             rows[prefix + 'is_correct_syntax'] = syn
             rows[prefix + 'exact_program_correct'] = exact
             out = {'syntax_acc': float(syn.mean()), 'exact_acc': float(exact.mean())}
             if not with_execution:
                 return out
+            if dev is not None:
+                rows[prefix + 'num_execution_correct'], rows[prefix + 'is_correct_execution'] = \
+                    dev['num_correct'], dev['is_correct']
+                out['hist'] = dev['hist']
+                if 'test_hist' in dev:
+                    rows['test_' + prefix + 'num_execution_correct'] = dev['test_num_correct']
+                    rows['test_' + prefix + 'is_correct_execution'] = dev['test_is_correct']
+                    out['test_hist'] = dev['test_hist']
+                return out
+            s_h = s_h_host()
+            if test is not None and 'test' not in cache:
+                cache['test'] = (test[0].astype(np.float32), test[1])
+            test_h = cache.get('test')
 
             def execute(first_frames, which, demo_k):
                 if karel:
@@ -1949,9 +1984,9 @@ class Model(object):
             num, ok, h_ = PM.compare_demo_and_execution(s_h, dlen, exe, exe_len, st['is_same_seq'])
             rows[prefix + 'num_execution_correct'], rows[prefix + 'is_correct_execution'] = num, ok
             out['hist'] = h_
-            if test is not None and (karel or 'test_init_pos' in host):
-                exe, exe_len = execute(test[0][:, :, 0], 'test_', test[0].shape[1])
-                num, ok, h_ = PM.compare_demo_and_execution(test[0], test[1], exe, exe_len, st['is_same_seq'])
+            if test_h is not None and (karel or 'test_init_pos' in host):
+                exe, exe_len = execute(test_h[0][:, :, 0], 'test_', test_h[0].shape[1])
+                num, ok, h_ = PM.compare_demo_and_execution(test_h[0], test_h[1], exe, exe_len, st['is_same_seq'])
                 rows['test_' + prefix + 'num_execution_correct'] = num
                 rows['test_' + prefix + 'is_correct_execution'] = ok
                 out['test_hist'] = h_

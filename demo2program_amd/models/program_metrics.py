@@ -3,7 +3,9 @@ execution accuracy.  In the reference these are tf.py_func callbacks inside the 
 (models/model_full.py:602-616 check_correct_syntax, :713-729 exact_program_compare_karel,
 :745-780 generate_program_output_karel, :878-901 CompareDemoAndExecution); they are logging /
 evaluation metrics, never part of the loss, so they stay on the host here too and work on the
-arrays the GPU path hands back (argmax tokens, lengths, is_same_seq).
+arrays the GPU path hands back (argmax tokens, lengths, is_same_seq).  For Karel, `karel_device_metrics` computes the
+syntax, execution and comparison results of these functions -- exactly -- in one device launch (csrc/karel_exec.hip);
+Model.report uses it unless D2P_HOST_PROGRAM_METRICS=1.
 
 Syntax and exact-program metrics exist for both DSLs (`parser_for`).  Execution is built in for
 Karel; the ViZDoom variant (model_full.py:789-848) drives whatever world object the caller's
@@ -11,6 +13,7 @@ Karel; the ViZDoom variant (model_full.py:789-848) drives whatever world object 
 without a factory `require_env` raises for it.
 """
 import numpy as np
+import torch
 
 from ..karel_env import Karel_world, parse
 
@@ -148,3 +151,44 @@ def compare_demo_and_execution(demo, demo_len, execution, execution_len, is_same
     num_correct = is_correct.sum(axis=1).astype(np.float32)
     hist = np.array([(num_correct == i).sum() / float(B) for i in range(k + 1)], np.float32)
     return num_correct, is_correct, hist
+
+
+def karel_device_metrics(p_token, p_len, is_same_seq, demos, demo_len, test_demos=None, test_demo_len=None,
+                         make_error=True):
+    """check_correct_syntax + generate_program_output + compare_demo_and_execution for Karel in one device launch
+    (kernels.karel_exec, csrc/karel_exec.hip), with the host functions' results exactly.
+
+    p_token [B, L], p_len [B], is_same_seq [B]: host arrays (the argmax tokens the caller already has).
+    demos [B, k, T, h, w, cs] uint8 / float32 and demo_len [B, k]: device tensors, read where they live (the feed);
+    test_demos / test_demo_len: the held-out demos, device tensors or None.
+    -> dict: syntax [B] float32, and per demo set (prefix '' and 'test_'): exec_len [B, k] int32, num_correct [B]
+    float32, is_correct [B, k] bool, hist [k+1] float32.  None when the launch does not take the geometry (the
+    caller then uses the host functions)."""
+    from .. import kernels as K
+    p_token = np.asarray(p_token)
+    B, L = p_token.shape
+    h, w = demos.shape[3:5]
+    if not K.karel_exec_supported(B, L, h, w, 16):
+        return None
+    # tokens, lengths and flags in one upload
+    host = np.empty(B * L + 2 * B, np.int32)
+    host[:B * L] = p_token.reshape(-1)
+    host[B * L:B * L + B] = np.asarray(p_len).reshape(-1)
+    host[B * L + B:] = np.asarray(is_same_seq).reshape(-1) != 0
+    buf = torch.from_numpy(host).to(demos.device)
+    k = demos.shape[1]
+    r = K.karel_exec(buf[:B * L].view(B, L), buf[B * L:B * L + B], buf[B * L + B:], demos, demo_len.reshape(B, k),
+                     test_demos, None if test_demos is None else test_demo_len.reshape(B, test_demos.shape[1]),
+                     make_error=make_error)
+    syntax, exec_len, is_correct, num = (r[n].cpu().numpy() for n in ('syntax', 'exec_len', 'is_correct',
+                                                                       'num_correct'))
+    out = {'syntax': syntax.astype(np.float32)}
+    for prefix, lo, hi, j in (('', 0, k, 0), ('test_', k, exec_len.shape[1], 1)):
+        if prefix and test_demos is None:
+            continue
+        n = num[:, j].astype(np.float32)
+        out[prefix + 'exec_len'] = exec_len[:, lo:hi]
+        out[prefix + 'num_correct'] = n
+        out[prefix + 'is_correct'] = is_correct[:, lo:hi] != 0
+        out[prefix + 'hist'] = np.array([(n == i).sum() / float(B) for i in range(hi - lo + 1)], np.float32)
+    return out

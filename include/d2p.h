@@ -566,6 +566,45 @@ int d2p_greedy_decode(int M, int U, int V, int L, const float* table_proj, const
                       const float* proj, const float* h0, const float* c0, int start_id, int end_id,
                       float* logits, int* ids, int* lengths, void* ws, size_t ws_bytes,
                       d2p_stream_t stream);
+/* ---- Karel program metrics (evaluation path, models/model_full.py:602-616,745-780,878-901) -------
+ * check_correct_syntax + generate_program_output + compare_demo_and_execution of
+ * models/program_metrics.py in one launch (one workgroup per row): each row's predicted tokens
+ * (tokens[b*ld_tok + i], i < clamp(p_len[b], 0, L); ids outside [0, 50) are a syntax error) are
+ * parsed by the stack machine of karel_env/dsl.py, run from the first frame of each of its demos
+ * (karel_env/karel.py; flags & D2P_KX_MAKE_ERROR = the make_error world) and compared with them.
+ * Two demo sets per call (the seen and the held-out demos); the second may be empty (k2 = 0):
+ *   frames  [B, k, T, h, w, cs] uint8 (flags & D2P_KX_U8) or float32, the first depth = 16 of cs
+ *           channels used; nonzero = true in frame 0; demo_len [B, k].  frames2 likewise.
+ * Outputs over the kk = k + k2 demos in that order (int32):
+ *   syntax [B] (1 for rows with is_same[b] != 0, without parsing), exec_len [B, kk] (1 + actions
+ *   of a successful run, 0 if the row is not run or the run fails), is_correct [B, kk]
+ *   (is_same || (exec_len == demo_len && all T demo frames equal the zero-padded execution)),
+ *   num_correct [B, 2] (sum of is_correct over each set); nullable: calls [B, kk] (the final call
+ *   counter), nframes [B, kk] (frames the run recorded, failed or not), execution [B, kk, T_out, h,
+ *   w, 16] float32 (generate_program_output's array; flags & D2P_KX_KEEP_FAILED keeps the frames a
+ *   failed run recorded).
+ * ws >= d2p_karel_exec_ws_bytes(B, L, h, w, depth), which is 0 for geometries the launch does not
+ * take (h*w > 64, L > 128, depth != 16): the caller then uses the host path.  After the launch
+ * ((const int*)ws)[b] holds row b's D2P_KX_* status bits (0 = the results are those of the host):
+ * NO_KAREL / COND_NO_KAREL = a run row had no Karel (where the host raises IndexError);
+ * PARSE_CAP / EXEC_CAP = a fixed step or stack bound was hit (the row failed).  Every loop is
+ * bounded whatever the tokens are.  No host synchronisation inside. */
+#define D2P_KX_MAKE_ERROR 1
+#define D2P_KX_U8 2
+#define D2P_KX_U8_2 4
+#define D2P_KX_KEEP_FAILED 8
+#define D2P_KX_NO_KAREL 1
+#define D2P_KX_COND_NO_KAREL 2
+#define D2P_KX_PARSE_CAP 4
+#define D2P_KX_EXEC_CAP 8
+size_t d2p_karel_exec_ws_bytes(int B, int L, int h, int w, int depth);
+int d2p_karel_exec(int B, int L, const int* tokens, int ld_tok, const int* p_len, const int* is_same,
+                   int h, int w, int depth, int flags,
+                   int k, int T, const void* frames, int cs, const int* demo_len,
+                   int k2, int T2, const void* frames2, int cs2, const int* demo2_len,
+                   int* syntax, int* exec_len, int* is_correct, int* num_correct,
+                   int* calls, int* nframes, float* execution, int T_out,
+                   void* ws, size_t ws_bytes, d2p_stream_t stream);
 /* ---- scheduled sampling step (models/model_full.py:59-67,414-423) -----------------------
  * seq2seq.ScheduledEmbeddingTrainingHelper.sample + next_inputs for one decoder step t:
  * next_ids[r] = Categorical(softmax(logits[r,:])) draw with probability *p_sample_dev, else
